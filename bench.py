@@ -13,10 +13,18 @@ micro-batch's statistics are resolved; here the loss head's backward is a few mi
 micro-batch's statistics are resolved once the next micro-batch is queued (every step's are read
 inside the timed region; the last one's before the closing synchronize).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     torchrun --nproc-per-node N bench.py --gpus N ...     (one rank per GPU)
 
-At N > 1, after the timed region, the trainer's exchange steps are measured on the real code
+A plain run does only what `value` needs: set up, warm up, time the K steps, print the line (with
+the loss kernel's roofline from the HIP events of those same steps).  --dump-outputs DIR then
+writes what the last timed step returned to its caller as DIR/<name>.npy (float32 / float64): loss,
+stats (_native.STATS order, without the slots only a value head fills), rows, and a fixed seeded
+sample of the gradient's rows (dlogits_sample, their row numbers in dlogits_sample_rows); the inputs are seeded, so two builds can be compared output for output.
+Everything below (the box copy beside the roofline, the CPU baselines, every probe) runs only with
+--full, where the --no-* options still switch single parts off.
+
+With --full at N > 1, after the timed region, the trainer's exchange steps are measured on the real code
 paths over the C2 model's parameter set (pipelinerl_amd/comm_probe.py) and reported under
 "exchange": the bucketed DP gradient all-reduce (GradBuckets, RCCL) and the trainer -> actors
 weight broadcast (WeightUpdateManager -> WorkerExtension, rank 0 -> ranks 1..N-1).
@@ -222,6 +230,34 @@ def make_workload(T: int, V: int, seq: int, prompt: int, seed: int, device):
         "overflow": torch.zeros((1, T), device=device),
     }
     return logits.requires_grad_(True), {k: v.contiguous() for k, v in fields.items()}
+
+
+DUMP_SAMPLE_BYTES = 48 << 20  # the gradient's sampled rows as float32; every file together < 64 MB
+
+
+# statistics slots that only a value head fills (rl.build_stats reads them with one only); the bench
+# passes no values, so they hold the reductions' identities (0, -inf / +inf), not results
+VALUE_HEAD_STATS = ("VALUE_LOSS", "VALUE_MEAN", "VALUE_MSE", "MAX_VALUE", "MIN_VALUE")
+
+
+def dump_outputs(out_dir: Path, last: dict, dlogits: torch.Tensor, stats_keep: list[int] | None = None) -> None:
+    """What the last timed step handed its caller, as float32 / float64 .npy files: grpo_loss's
+    returns (loss, stats, rows [8, T - 1]) and the gradient it left in logits.grad, of which a fixed
+    seeded sample of whole rows is kept (dlogits_sample_rows: their row numbers).  ``stats_keep``:
+    the statistics' slots to write, in order (default: all)."""
+    out_dir.mkdir(parents=True, exist_ok=True)
+    T, V = dlogits.shape[-2], dlogits.shape[-1]
+    n = max(1, min(T, DUMP_SAMPLE_BYTES // (4 * V)))
+    picked = np.sort(np.random.default_rng(20240229).choice(T, size=n, replace=False))
+    idx = torch.from_numpy(picked).to(dlogits.device)
+    stats = last["stats"].double()
+    if stats_keep is not None:
+        stats = stats[stats_keep]
+    arrays = {"loss": last["loss"].detach().float().reshape(1), "stats": stats,
+              "rows": last["rows"].float(), "dlogits_sample": dlogits.reshape(T, V).index_select(0, idx).float(),
+              "dlogits_sample_rows": idx.double()}
+    for name, t in arrays.items():
+        np.save(out_dir / f"{name}.npy", t.cpu().numpy())
 
 
 def cpu_baseline(rows: int, V: int, threads: int, min_seconds: float = 10.0, max_reps: int = 16) -> dict:
@@ -487,6 +523,10 @@ def main():
     ap.add_argument("--tokens", type=int, default=65536)
     ap.add_argument("--vocab", type=int, default=151936)
     ap.add_argument("--cpu-rows", type=int, default=4096)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs as DIR/<name>.npy (rank 0)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what is reported beside `value`: the box copy, the CPU baselines, every probe")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-comm-probe", action="store_true", help="N > 1: skip the all-reduce / broadcast probes")
     ap.add_argument("--no-trainer-step", action="store_true", help="skip the full trainer-step probe")
@@ -496,6 +536,9 @@ def main():
     ap.add_argument("--no-split-pipeline", action="store_true",
                     help="N > 1: skip the split trainer/actor probe (configs[3]: 7B, overlapped weight broadcast)")
     args = ap.parse_args()
+    if not args.full:  # a plain run: the timed steps and their line only
+        args.no_cpu_baseline = args.no_comm_probe = args.no_trainer_step = args.no_c3 = True
+        args.no_fsdp = args.no_fp32 = args.no_split_pipeline = True
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -533,16 +576,19 @@ def main():
 
     host_stats = [torch.empty(NSTAT, dtype=torch.float64, pin_memory=True) for _ in range(2)]
     resolved = []
+    last = {}  # --dump-outputs: what the latest step returned
 
     def step(timed: bool, i: int):
         logits.grad = None
         if timed:
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             e0.record()
-        loss, stats, _ = grpo_loss(logits, fields, params)
+        loss, stats, rows = grpo_loss(logits, fields, params)
         if timed:
             e1.record()
             fwd_ev.append((e0, e1))
+            if args.dump_outputs:
+                last.update(loss=loss, stats=stats, rows=rows)
         host_stats[i % 2].copy_(stats, non_blocking=True)  # the one statistics read-back per micro-batch
         copied = torch.cuda.Event()
         copied.record()
@@ -585,11 +631,17 @@ def main():
         dist.all_reduce(k_max, op=dist.ReduceOp.MAX)
     elapsed = float(t_max)
     kern_ms = float(k_max)
-    # the same bytes through a plain device copy on this box (torch's copy kernel, logits -> a second
-    # buffer: one read + one write of T x V bf16), after the timed region: HBM rates vary a few %
+    if args.dump_outputs and rank == 0:
+        from pipelinerl_amd._native import STATS
+
+        dump_outputs(Path(args.dump_outputs), last, logits.grad,
+                     stats_keep=[i for i, name in enumerate(STATS) if name not in VALUE_HEAD_STATS])
+    last.clear()
+    # --full: the same bytes through a plain device copy on this box (torch's copy kernel, logits -> a
+    # second buffer: one read + one write of T x V bf16), after the timed region: HBM rates vary a few %
     # from box to box, and this puts the loss head's rate beside a copy measured in the same run
     copy_ms = None
-    if rank == 0:
+    if rank == 0 and args.full:
         dst = torch.empty_like(logits)
         cts = []
         for i in range(8):
@@ -609,7 +661,8 @@ def main():
     # microbenchmarks), so a driver lease that runs out loses the least important ones.
     import datetime
 
-    ctrl = dist.new_group(backend="gloo", timeout=datetime.timedelta(seconds=300)) if world > 1 else None
+    ctrl = dist.new_group(backend="gloo", timeout=datetime.timedelta(seconds=300)) \
+        if world > 1 and args.full else None
     # a probe stuck in a collective is cut off after this long (N > 1; torch's RCCL watchdog: 10 min)
     deadline = float(os.environ.get("PRL_BENCH_PROBE_DEADLINE_S", "480")) if world > 1 else None
     runner = ProbeRunner(rank, dev, ctrl, deadline_s=deadline)
@@ -618,7 +671,7 @@ def main():
     logits = fields = None
     torch.cuda.empty_cache()
     census = None
-    if world > 1:
+    if world > 1 and args.full:
         # every communicator of the run reports the size it was meant to have (and that many ranks
         # take part in an all-reduce over it) before any probe relies on it
         census = optional("communicators", lambda: communicator_census(world, ctrl, dev, prl_comm=not rehearse))
@@ -740,6 +793,7 @@ def main():
             "n_gpus": world,
             "steps": args.steps,
             "warmup": args.warmup,
+            "full": args.full,
             "ms_per_step": round(ms_per_step, 4),
             "higher_is_better": True,
             "scaling": "weak",

@@ -25,6 +25,15 @@ def _tiny():
     return Qwen2ForCausalLM(cfg).to(torch.bfloat16)
 
 
+def _leave():
+    """End a spawned rank once its results are on disk: no gloo teardown (destroy_process_group, the
+    interpreter's exit), which aborted a rank of the c3_dp run once ("terminate called without an
+    active exception", after its last collective) on a loaded machine, as in test_weight_update_cpu."""
+    sys.stdout.flush()
+    sys.stderr.flush()
+    os._exit(0)
+
+
 def _run(rank, port, world, actors, out):
     sys.path[:0] = [str(ROOT), str(ROOT / "pipelinerl-swe_amd"), str(ROOT / "tests")]
     os.environ["OMP_NUM_THREADS"] = "1"
@@ -54,7 +63,7 @@ def _run(rank, port, world, actors, out):
                                make_trainer=make_trainer, make_actor_module=make_actor, packer=TorchFlatPacker())
     params = {n: p.detach().clone() for n, p in holder["model"].named_parameters()}
     torch.save({"res": res, "params": params}, Path(out) / f"r{rank}.pt")
-    dist.destroy_process_group()
+    _leave()
 
 
 @pytest.mark.parametrize("world,actors", [(2, 1), (4, 2), (8, 4)])  # (8, 4): C4 on one node
@@ -96,7 +105,7 @@ def _fsdp_run(rank, port, world, out):
     sec = ts.timed(2, 1)
     full = {n: p.detach().full_tensor().clone() for n, p in ts.model.named_parameters()}
     torch.save({"sec": sec, "params": full}, Path(out) / f"f{rank}.pt")
-    dist.destroy_process_group()
+    _leave()
 
 
 def test_fsdp_trainer_step_gloo(tmp_path):
@@ -126,7 +135,7 @@ def _dp_run(rank, port, world, out):
     res = dp_step_probe("c3", steps=2, warmup=1, device="cpu", samples_per_step=64, batches=batches,
                         model=_tiny().float(), step_fn=cpu_rl_step)
     torch.save(res, Path(out) / f"dp{rank}.pt")
-    dist.destroy_process_group()
+    _leave()
 
 
 def test_c3_dp_probe_gloo(tmp_path):

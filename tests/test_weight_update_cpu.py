@@ -36,6 +36,79 @@ def free_port():
     return p
 
 
+def record_rendezvous(scheme, port, world):
+    """Registers ``scheme://`` as a rendezvous over the trainer's TCP store (this process a client)
+    behind a store that notes every key it is asked about; returns the list of "op key" notes."""
+    from datetime import timedelta
+
+    import torch.distributed as dist
+
+    notes, alive = [], []
+
+    class RecordingStore(dist.Store):
+        def __init__(self, inner):
+            super().__init__()
+            self.inner = inner
+
+        def set(self, key, value):
+            notes.append(f"set {key}")
+            self.inner.set(key, value)
+
+        def get(self, key):
+            notes.append(f"get {key}")
+            return self.inner.get(key)
+
+        def add(self, key, value):
+            notes.append(f"add {key}")
+            return self.inner.add(key, value)
+
+        def compare_set(self, key, expected, desired):
+            notes.append(f"compare_set {key}")
+            return self.inner.compare_set(key, expected, desired)
+
+        def wait(self, keys, timeout=None):
+            notes.extend(f"wait {k}" for k in keys)
+            return self.inner.wait(keys) if timeout is None else self.inner.wait(keys, timeout)
+
+        def check(self, keys):
+            notes.extend(f"check {k}" for k in keys)
+            return self.inner.check(keys)
+
+        def delete_key(self, key):
+            notes.append(f"delete_key {key}")
+            return self.inner.delete_key(key)
+
+        def append(self, key, value):
+            notes.append(f"append {key}")
+            self.inner.append(key, value)
+
+        def multi_get(self, keys):
+            notes.extend(f"multi_get {k}" for k in keys)
+            return self.inner.multi_get(keys)
+
+        def multi_set(self, keys, values):
+            notes.extend(f"multi_set {k}" for k in keys)
+            self.inner.multi_set(keys, values)
+
+        def num_keys(self):
+            return self.inner.num_keys()
+
+        def set_timeout(self, timeout):
+            self.inner.set_timeout(timeout)
+
+        def has_extended_api(self):
+            return self.inner.has_extended_api()
+
+    def handler(url, timeout=timedelta(seconds=300), **kwargs):
+        rank = int(url.split("rank=")[1].split("&")[0])
+        store = RecordingStore(dist.TCPStore("127.0.0.1", port, world, False, timeout=timeout))
+        alive.append(store)  # the group keeps the C++ half only: the overrides live in the Python object
+        yield store, rank, world
+
+    dist.register_rendezvous_handler(scheme, handler)
+    return notes
+
+
 def make_model(seed):
     torch.manual_seed(seed)
     m = torch.nn.Sequential(torch.nn.Embedding(37, 16), torch.nn.Linear(16, 24), torch.nn.LayerNorm(24),
@@ -100,13 +173,20 @@ def _actor(port, world, idx, transport, exp, nupdates, use_reference_pg, qwen=Fa
                     "fused": {n: p.clone() for n, p in m.params.items()}}, Path(exp) / f"actor{idx}_params.pt")
         return
     worker = StandaloneWorker(make_model(100 + idx), rank=0, device="cpu", backend="gloo")
-    if use_reference_pg:  # join with the REFERENCE's group helper: pins the store-key layout
-        sys.path.insert(0, "/root/reference")
-        from pipelinerl.torch_utils import init_extra_process_group as ref_init
+    keys = None
+    # use_reference_pg: False = the worker's own join; None = the project's group helper over a recording
+    # store (pins the store-key layout); a path = the same through that reference checkout's helper
+    if use_reference_pg is not False:
+        keys = record_rendezvous("rec", port, world)
+        if use_reference_pg:  # golden/make_actor_group_keys.py: a reference checkout's own group helper
+            sys.path.insert(0, use_reference_pg)
+            from pipelinerl.torch_utils import init_extra_process_group as join
+        else:
+            from pipelinerl_amd.torch_utils import init_extra_process_group as join
 
         worker.pg_rank = 1 + idx
-        worker.process_group = ref_init(group_name="actor", backend="gloo", init_method=f"tcp://127.0.0.1:{port}",
-                                        rank=worker.pg_rank, world_size=world)
+        worker.process_group = join(group_name="actor", backend="gloo", init_method="rec://actor",
+                                    rank=worker.pg_rank, world_size=world)
     else:
         worker.init_actor_update_group(idx, 1, f"tcp://127.0.0.1:{port}", world)
     names = [(n, list(p.shape)) for n, p in worker.model_runner.model.params.items()]
@@ -116,6 +196,8 @@ def _actor(port, world, idx, transport, exp, nupdates, use_reference_pg, qwen=Fa
                                                          bucket_bytes=1000 if transport == "bucketed" else 0))
     torch.save({n: p.detach().clone() for n, p in worker.model_runner.model.params.items()},
                Path(exp) / f"actor{idx}_params.pt")
+    if keys is not None:
+        (Path(exp) / f"actor{idx}_keys.json").write_text(json.dumps(sorted(set(keys))))
     os._exit(0)  # no gloo teardown at interpreter exit (it aborted once under a loaded pytest -n 4)
 
 
@@ -203,15 +285,19 @@ def test_fused_direct_target_matches_the_stand_in():
     assert resolve("no.such.param", (1,)) is None
 
 
-@pytest.mark.skipif(not Path("/root/reference/pipelinerl/torch_utils.py").exists(),
-                    reason="reference checkout not present (wire-compat check runs in the build container)")
 def test_actor_group_interoperates_with_reference_helper(tmp_path):
+    """An actor that joins the trainer's "actor" group through the project's helper touches exactly
+    the rendezvous-store keys the reference's helper touches in that place (recorded with it:
+    golden/actor_group_store_keys.json, golden/make_actor_group_keys.py), and the weights arrive."""
     port = free_port()
-    mp.spawn(_run, args=(port, 2, "per_tensor", str(tmp_path), True), nprocs=2, join=True)
+    mp.spawn(_run, args=(port, 2, "per_tensor", str(tmp_path), None), nprocs=2, join=True)
     want = torch.load(tmp_path / "trainer_params.pt")
     got = torch.load(tmp_path / "actor0_params.pt")
     for n in want:
         assert torch.equal(got[n], want[n].to(torch.bfloat16)), n
+    golden = json.loads((ROOT / "tests" / "golden" / "actor_group_store_keys.json").read_text())
+    assert golden["group_name"] == "actor" and golden["world_size"] == 2 and golden["rank"] == 1
+    assert json.loads((tmp_path / "actor0_keys.json").read_text()) == golden["keys"]
 
 
 def _failing_trainer(port, exp, mode):

@@ -1,5 +1,6 @@
 """Diagnostic: bench.py with GradBuckets' side stream at normal priority (the round-5 setting), for
-the one-GPU multi-rank rehearsal A/B.  Usage as bench.py (torch.distributed.run … this file …)."""
+the one-GPU multi-rank rehearsal A/B.  Usage as bench.py (torch.distributed.run … this file …
+--full: GradBuckets runs in the bench's probes only)."""
 import runpy
 import sys
 from pathlib import Path

@@ -45,7 +45,7 @@ def main(fetch_dir: str, write_dir: str, out: str) -> None:
            "read_bytes_corrected": rd, "write_bytes": wr, "bytes_per_launch": rd + wr,
            "algorithmic_bytes": alg, "traffic_over_algorithmic": (rd + wr) / alg,
            "method": "rocprofv3 --pmc FETCH_SIZE and --pmc WRITE_SIZE in separate passes, --output-format csv, "
-                     "bench.py --steps 3 --warmup 1 --no-cpu-baseline; FETCH_SIZE x1024 x2 (gfx950 half-count on "
+                     "bench.py --full --steps 3 --warmup 1 --no-cpu-baseline; FETCH_SIZE x1024 x2 (gfx950 half-count on "
                      "16-B/lane streaming reads), WRITE_SIZE x1024; mean over launches",
            "launches": n}
     Path(out).write_text(json.dumps(res, indent=1))
